@@ -120,6 +120,23 @@ def run_steps(B, params, sched, trap_p, x, T, nsteps, seed, index_base, precisio
     return launches
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, x):
+    """--dump-outputs: the rotations the timed chain left in x (what p_sample_prepared hands its caller), as out_dir/rotations.npy
+    in float32.  A batch larger than DUMP_MAX_BYTES is written as a seed-0 sample of its rows, in index order, with the row
+    indices beside it (sample_rows.npy, float64): the same rows for the same --batch-log2, so two builds compare row for row."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, row_bytes = x.shape[0], x[0].numel() * 4
+    if n * row_bytes > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 1024) // (row_bytes + 8)   # the sampled rows, their float64 indices and two .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        np.save(os.path.join(out_dir, "sample_rows.npy"), idx.astype(np.float64))
+        x = x[torch.from_numpy(idx).to(x.device)]
+    np.save(os.path.join(out_dir, "rotations.npy"), x.float().cpu().numpy())
+
+
 def cpu_baseline(T, params_np, betas, budget_s=6.0):
     """The oracle (C restatement, OpenMP over the batch, all host threads) timed on this box's host cores on a bounded sample of
     the same workload: 2^17 rotations x as many reverse steps around the middle of the chain as ~6 s of CPU work hold.  The timed
@@ -898,6 +915,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--train-timeout", type=float, default=240.0, help="N > 1: seconds the training leg may take before the line is printed without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the rotations the timed steps leave (rank 0) as DIR/rotations.npy")
     args = ap.parse_args()
 
     from so3x import backend as B
@@ -961,6 +979,8 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     el, el_fastest = float(tmax[0].item()), -float(tmax[1].item())
     ok = bool(torch.isfinite(x).all().item())
+    if args.dump_outputs and ctx.rank == 0:   # before the roofline launches below step x further
+        dump_outputs(args.dump_outputs, x)
 
     # ---- roofline of the dominant kernel on a FIXED shape (100 steps per launch, 5 launches, HIP events on the launch
     #      stream): the shape the rocprofv3 summaries under profiles/ were taken on, whatever --steps was

@@ -415,6 +415,7 @@ def test_bench_gpus_n_starts_its_own_ranks_without_touching_a_gpu():
     fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "_self_launch")
     assert not any(isinstance(n, (ast.Import, ast.ImportFrom)) and any(a.name.split(".")[0] == "torch" for a in n.names) for n in ast.walk(fn))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = "-1"   # no device for the children on a GPU machine either
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--no-extras"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode != 0
@@ -454,3 +455,23 @@ def test_prepared_cache_sees_writes_that_tensor_versions_miss():
     m = len(built)
     c2.get("k", flat, build)
     assert len(built) == m + 1                       # idle gap
+
+
+def test_bench_dump_outputs_writes_the_batch_or_a_fixed_sample_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole batch as float32 while it fits in DUMP_MAX_BYTES; past that, the same seeded rows every
+    time, in index order, their indices beside them, and the files together within the cap."""
+    import bench
+    x = torch.randn(1000, 3, 3)
+    bench.dump_outputs(str(tmp_path / "all"), x)
+    assert sorted(os.listdir(tmp_path / "all")) == ["rotations.npy"]
+    got = np.load(tmp_path / "all" / "rotations.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x)
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    assert 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    got = np.load(tmp_path / "a" / "rotations.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy()[rows.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 20_000

@@ -7,7 +7,7 @@
 #     counters-only build whose gathers are forced onto distinct bank groups (-DFUSED_AB_TAB_SPREAD; same instruction stream).
 # Needs $R/build/libso3x_tabspread.so:   tools/ab/build_variant.sh tabspread "-DFUSED_AB_TAB_SPREAD" so3x_train_fused.hip
 name=${1:-fused_bounds}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
 bash $R/tools/pmc_quick.sh ${name}_drawn tools/ab/ab_fused_libs.py $R/diffusion-extensions_amd/libso3x.so > /dev/null
 bash $R/tools/pmc_quick.sh ${name}_tconst tools/ab/ab_fused_libs.py $R/diffusion-extensions_amd/libso3x.so --t-const > /dev/null
 bash $R/tools/pmc_quick.sh ${name}_tabspread tools/ab/ab_fused_libs.py $R/build/libso3x_tabspread.so > /dev/null

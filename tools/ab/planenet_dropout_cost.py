@@ -1,6 +1,6 @@
 """One PlaneNet bf16 training evaluation (forward with stash + backward) at 32 x 2048 with and without the reference's dropout 0.1."""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "diffusion-extensions_amd")):
     sys.path.insert(0, p)
 import torch

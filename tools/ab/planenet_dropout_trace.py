@@ -1,7 +1,7 @@
 """bf16 PlaneNet training evaluations at 32 x 2048 with a given dropout probability, for a kernel trace (what dropout costs, kernel by kernel):
    rocprofv3 --kernel-trace --output-format csv -d out -o p -- python3 tools/ab/planenet_dropout_trace.py 0.1   (and 0.0)"""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "diffusion-extensions_amd")):
     sys.path.insert(0, p)
 import torch

@@ -1,7 +1,7 @@
 """bf16 PlaneNet inference at 32 x 2048: the LayerNorm-folded path (no stash) against the plain kernel sequence (what a forward with
 a stash runs), same process, interleaved."""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "diffusion-extensions_amd")):
     sys.path.insert(0, p)
 import torch

@@ -1,6 +1,6 @@
 """bf16 PlaneNet training evaluation at the reference's default shape (32 x 256) in a loop, for rocprofv3 --kernel-trace --stats"""
 import os, sys, time
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "diffusion-extensions_amd")):
     sys.path.insert(0, p)
 import torch

@@ -1,7 +1,7 @@
 """PlaneNet bf16 training evaluation (forward with stash + backward) at 32 x 2048 for a kernel trace:
 rocprofv3 --kernel-trace --stats --output-format csv -d out -o t -- python3 tools/ab/planenet_train_trace.py"""
 import os, sys
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in (ROOT, os.path.join(ROOT, "diffusion-extensions_amd")):
     sys.path.insert(0, p)
 import torch

@@ -1,6 +1,6 @@
 """bf16 vs exact-fp32 ProtNet forward on the same weights: where the difference sits (encoder output per chain / head input / output)"""
 import sys, os
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, ROOT + "/diffusion-extensions_amd", ROOT + "/tests"]
 import torch, warnings; warnings.filterwarnings("ignore")
 from test_protnet import synthetic_complexes, to_dev, protnet_perturb

@@ -7,7 +7,7 @@
 #   tools/ab/build_variant.sh wide_2x "-DRESNET_AB_2X" so3x_resnet.hip
 #   tools/ab/build_variant.sh wide_noy_2x "-DRESNET_AB_NO_Y -DRESNET_AB_2X" so3x_resnet.hip
 # The builds compute garbage gradients; only their times count.  The library is swapped on the box's scratch copy only.
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/../.." && pwd)
 lib=$R/diffusion-extensions_amd/libso3x.so
 cp $lib /tmp/libso3x_product.so
 for round in 1 2; do

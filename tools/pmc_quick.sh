@@ -1,7 +1,7 @@
 #!/bin/bash
 # quick PMC passes over one command: tools/pmc_quick.sh <out-name> <script and args...>   (run through gpurun from the repo root)
 name=$1; shift
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/$name
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 #   tools/profile_round.sh r01      ->  gpurun_out/profile_r01/{bench_line.json, stats/, pmc_*/}
 # then `python tools/summarize_profiles.py r01` (no GPU needed) copies the summaries into profiles/.
 tag=${1:-r01}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/profile_$tag
 mkdir -p $out
 cd $R
